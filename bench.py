@@ -15,6 +15,12 @@ Each timed step is the full training step: on-device synthetic batch generation,
 both towers, cross-GPU all-gather of embeddings, MIL-NCE on the global batch, backward with
 bucketed RCCL gradient all-reduce, fused Adam, LR schedule. Rank 0 prints ONE JSON line; the
 value is the whole-job aggregate video-text pairs/s (max step time over ranks).
+
+A plain run sets up, warms up, times the K steps and prints the line. ``--dump-outputs DIR`` also
+writes what the last timed step computed (``_dump_outputs``); the inputs and initial weights are
+functions of the arguments alone, so two builds can be compared output for output. ``--full`` adds
+the measurements the headline figure does not need: at N > 1 the step's collectives timed alone
+(``"comm"``) and the kernel-plan digest gathered from every rank.
 """
 from __future__ import annotations
 
@@ -31,6 +37,35 @@ def _native_lib() -> str:
     """File name of the HIP kernel library this process loaded (there is no fallback path)."""
     from mil_nce_howto100m_amd.ops import _lib
     return os.path.basename(_lib.LIB_PATH)
+
+
+DUMP_SAMPLE = 2 << 20  # elements kept of the flat parameters (8 MiB as fp32 + 16 MiB of indices)
+
+
+def _dump_outputs(out_dir: str, trainer, losses) -> None:
+    """What the last timed step left its caller, as ``<name>.npy`` files: ``loss`` (the step's
+    return value), ``losses`` (every timed step's) and ``param`` (the parameters after the last
+    update, flattened in ``model.parameters()`` order), all float32. A ``param`` longer than
+    DUMP_SAMPLE is sampled at fixed seeded indices, written as ``param_index`` (float64, the same
+    for every run of one configuration)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+    vals = torch.stack([l.detach().float().reshape(()) for l in losses]).cpu().numpy() if losses \
+        else np.zeros(0, np.float32)
+    save("losses", vals.astype(np.float32))
+    save("loss", vals[-1:].astype(np.float32))
+    net = trainer.model.module if hasattr(trainer.model, "module") else trainer.model
+    flat = torch.cat([p.detach().reshape(-1).float() for p in net.parameters()])
+    if flat.numel() > DUMP_SAMPLE:
+        idx = np.unique(np.random.default_rng(0).integers(0, flat.numel(), DUMP_SAMPLE))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+        save("param_index", idx.astype(np.float64))
+    save("param", flat.cpu().numpy())
 
 
 def main():
@@ -55,6 +90,12 @@ def main():
                          "(same-box A/B: 4592 vs 4677 pairs/s without, profiles/r5_launch_merge.md)")
     ap.add_argument("--save_plan", type=str, default="",
                     help="write this run's kernel-plan decisions as a plan table (ops/tune_sync.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: at N > 1 the step's collectives "
+                         "timed alone (\"comm\") and the kernel-plan digest of every rank")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps write what the last timed step computed (its loss and the "
+                         "updated parameters) as DIR/<name>.npy")
     opts = ap.parse_args()
 
     if opts.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -131,14 +172,16 @@ def main():
     dt = time.perf_counter() - t0
     dt = pdist.all_reduce_max(dt)
     final_loss = float(losses[-1].item()) if losses else float("nan")
+    if opts.dump_outputs and ctx.is_main:
+        _dump_outputs(opts.dump_outputs, trainer, losses)
     # kernel plan of every rank (ops/tune_sync: rank 0 tunes, the others launch its choices)
     from mil_nce_howto100m_amd.ops import tune_sync
     hashes = [tune_sync.plan_hash()]
-    if ctx.world_size > 1:
+    if opts.full and ctx.world_size > 1:
         hashes = [None] * ctx.world_size
         torch.distributed.all_gather_object(hashes, tune_sync.plan_hash())
     comm = None
-    if ctx.world_size > 1:
+    if opts.full and ctx.world_size > 1:
         # after the timed region: the step's collectives alone at the step's sizes (xGMI record)
         from mil_nce_howto100m_amd.parallel.comm_probe import probe
         net = trainer.model.module if hasattr(trainer.model, "module") else trainer.model

@@ -45,7 +45,7 @@ def _clean_env():
 def test_bench_self_launches_n_ranks(world):
     """bench.py --gpus N as its own launcher: N ranks, one JSON line, the world size observed by
     torch.distributed; W = 8 is the driver's scaling-run shape (rehearsed on gloo here)."""
-    cmd = [sys.executable, "bench.py", "--gpus", str(world), "--steps", "1", "--warmup", "1", *TINY]
+    cmd = [sys.executable, "bench.py", "--gpus", str(world), "--steps", "1", "--warmup", "1", "--full", *TINY]
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=_clean_env())
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
